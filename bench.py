@@ -11,12 +11,25 @@ A "step" is one pass of the hot path over the staged dataset: the filter
 program is evaluated over every block's rows in ONE kernel launch, with
 inputs already resident in HBM.  value = whole-job matched rows/sec across
 all ranks (the headline filters match every generated row by construction,
-so matched == scanned there; both fields are reported).  The bench is
-self-checking at full size: a selective phrase whose expected count was
-recorded by the data generator (gen_manifest.json, computed with plain
-string find — independent of every scan path) must match exactly.
+so matched == scanned there; both fields are reported, and the all-match
+invariant is asserted on every run).
+
+A plain run does only what the headline figure needs: open the cached
+fixture, stage it, warm up, time the steps, print the result line.  --full
+adds the legs that take runs of their own: the full-size selectivity
+self-check (a selective phrase whose expected count was recorded by the data
+generator — gen_manifest.json, computed with plain string find, independent
+of every scan path — must match exactly) and the CPU-oracle baseline.
+
+The fixture is cached under --data-dir (default build/bench_data in this
+tree); `bench.py --prepare-data` generates it without touching a GPU, and
+build() does so on GPU hosts, so a benchmark run does not pay for it.
+
+--dump-outputs DIR writes what the last timed step computed as float .npy
+files (see dump_outputs()) so two builds can be compared output for output.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R]
+                       [--full] [--dump-outputs DIR]
 For N>1 the driver launches this under torch.distributed.run, one rank per
 GPU; the only collective is an all_reduce(SUM) of matched-row counters
 (RCCL over xGMI).
@@ -29,7 +42,15 @@ import sys
 import time
 from concurrent.futures import ThreadPoolExecutor
 
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, ROOT)
+
+# fixture cache: inside the tree's (git-ignored) build directory, so it sits
+# next to the libraries build() produced and `make clean` removes it
+DEFAULT_DATA_DIR = os.path.join(ROOT, "build", "bench_data")
+
+# --dump-outputs budget: the bitmaps are the only large array
+DUMP_MAX_BITMAP_VALUES = 15_000_000  # float32 => 60 MB of the 64 MB allowed
 
 HBM_PEAK_BYTES_PER_S = 8.0e12  # MI355X spec peak (MI355X_MICROARCH.md)
 
@@ -93,6 +114,12 @@ def log(msg):
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
 
 
+def bench_nparts(rows, world):
+    """Number of parts one rank's shard is split into."""
+    return max(1, min(64, (os.cpu_count() or 8) // max(1, world),
+                      max(8, rows // 16_000_000)))
+
+
 def prepare_parts(data_dir, total_rows, nparts, msg_len, seed_base):
     """Generates nparts reference-format parts in parallel (cached on disk;
     gen_manifest.json is written last and doubles as a completion marker)."""
@@ -129,7 +156,7 @@ def stream_stages(data_dir, total_rows, nparts, msg_len, seed_base, filt,
     hold a 1B-row fixture (~65 GB of zstd parts plus headroom), but its HBM
     can hold the staged columns (~260 GB) — so parts stream through the disk
     while the staged arena accumulates.  One kernel launch per part-stage.
-    Returns (stages, manifest_totals, rows, gen_stage_s)."""
+    Returns (stages, manifest_totals, rows, gen_stage_s, dims)."""
     import shutil
     from concurrent.futures import ThreadPoolExecutor
 
@@ -146,6 +173,7 @@ def stream_stages(data_dir, total_rows, nparts, msg_len, seed_base, filt,
     ahead = min(16, nparts)
     t0 = time.time()
     stages = []
+    dims = []
     manifests = {}
     total = 0
     with ThreadPoolExecutor(max_workers=ahead) as ex:
@@ -172,6 +200,7 @@ def stream_stages(data_dir, total_rows, nparts, msg_len, seed_base, filt,
                     manifests[k] = manifests.get(k, 0) + v
             p = Part(d)
             st = Stage(p, filt, device=device)
+            dims.append(part_dims(p))
             p.close()  # staging holds everything in HBM; files can go
             stages.append(st)
             total += st.rows
@@ -179,7 +208,72 @@ def stream_stages(data_dir, total_rows, nparts, msg_len, seed_base, filt,
             if i % 8 == 0:
                 log(f"streamed part {i + 1}/{len(specs)} "
                     f"({total} rows staged)")
-    return stages, manifests, total, time.time() - t0
+    return stages, manifests, total, time.time() - t0, dims
+
+
+def remove_partial_parts(rank_dir):
+    """gen_manifest.json is written last; its absence marks a partial part
+    stranded by a failed generation."""
+    import glob
+    import shutil
+    for d in glob.glob(os.path.join(rank_dir, "part_*")):
+        if not os.path.exists(os.path.join(d, "gen_manifest.json")):
+            shutil.rmtree(d, ignore_errors=True)
+
+
+def prepare_data(args):
+    """--prepare-data: generates the single-GPU fixture a plain run would
+    otherwise generate first, and nothing else (no GPU, no torch)."""
+    rank_dir = os.path.join(args.data_dir, "rank0")
+    try:
+        prepare_parts(rank_dir, args.rows, bench_nparts(args.rows, 1),
+                      args.msg_len, seed_base=1)
+    except RuntimeError as e:
+        if "short write" not in str(e):
+            raise
+        # the benchmark streams parts through a disk this small
+        log(f"disk too small to cache the fixture ({e}); not cached")
+        remove_partial_parts(rank_dir)
+
+
+def part_dims(part):
+    """(blocks, bitmap words) of a part: one bitmap per block, padded to
+    whole 64-bit words (the layout vql_fetch_bitmaps returns)."""
+    nblocks = part.blocks
+    return nblocks, sum((part.block_rows(i) + 63) // 64
+                        for i in range(nblocks))
+
+
+def dump_outputs(out_dir, stages, dims, last_hits, suffix=""):
+    """Writes what a caller of the timed path holds after its last step:
+
+    hits.npy       float64[stages]  matched rows each scan() returned
+    block_hits.npy float64[blocks]  per-block matched rows
+    bitmaps.npy    float32[words*4] the result bitmaps, 16 bits per value
+                   (little-endian: value k of word w holds rows 64w+16k ..
+                   64w+16k+15 of the block), so every value is exact
+
+    Past DUMP_MAX_BITMAP_VALUES the bitmaps are reduced to a fixed seeded
+    sample of their 16-bit values (same positions on every run)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    block_hits = []
+    chunks = []
+    for st, (nblocks, nwords) in zip(stages, dims):
+        block_hits.extend(st.fetch_block_hits(nblocks))
+        chunks.append(np.frombuffer(st.fetch_bitmaps(nwords), dtype="<u2"))
+    bits = np.concatenate(chunks) if chunks else np.zeros(0, dtype="<u2")
+    if bits.size > DUMP_MAX_BITMAP_VALUES:
+        idx = np.unique(np.random.default_rng(0).integers(
+            0, bits.size, DUMP_MAX_BITMAP_VALUES))
+        bits = bits[idx]
+    np.save(os.path.join(out_dir, f"hits{suffix}.npy"),
+            np.asarray(last_hits, dtype=np.float64))
+    np.save(os.path.join(out_dir, f"block_hits{suffix}.npy"),
+            np.asarray(block_hits, dtype=np.float64))
+    np.save(os.path.join(out_dir, f"bitmaps{suffix}.npy"),
+            bits.astype(np.float32))
 
 
 def read_manifests(part_dirs):
@@ -267,9 +361,21 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS),
                     default="phrase_regex")
     ap.add_argument("--data-dir", default=os.environ.get(
-        "VQL_DATA_DIR", "/tmp/vql_bench_data"))
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
-    ap.add_argument("--skip-selectivity", action="store_true")
+        "VQL_DATA_DIR", DEFAULT_DATA_DIR))
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: "
+                         "the full-size selectivity self-check and the CPU "
+                         "oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step "
+                         "computed as DIR/<name>.npy")
+    ap.add_argument("--prepare-data", action="store_true",
+                    help="generate the cached single-GPU fixture for "
+                         "--rows/--msg-len and exit (needs no GPU)")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baseline out")
+    ap.add_argument("--skip-selectivity", action="store_true",
+                    help="with --full: leave the selectivity check out")
     ap.add_argument("--stream-parts", action="store_true",
                     help="generate->stage->delete parts one at a time so "
                          "configs whose fixture exceeds the box disk (1B "
@@ -277,6 +383,14 @@ def main():
                          "--skip-cpu-baseline/--skip-selectivity (the part "
                          "files are gone after staging)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.prepare_data:
+        prepare_data(args)
+        return
+    if not args.full:
+        args.skip_cpu_baseline = True
+        args.skip_selectivity = True
 
     import torch
     import torch.distributed as dist
@@ -306,15 +420,15 @@ def main():
 
     # Each rank generates and stages its own shard (weak scaling; blocks are
     # independent units, storage_search.go:1035-1067).
-    nparts = max(1, min(64, (os.cpu_count() or 8) // max(1, world),
-                        max(8, args.rows // 16_000_000)))
+    nparts = bench_nparts(args.rows, world)
     filt = Filter(filter_json)
+    dims = []  # per-stage (blocks, bitmap words), for --dump-outputs
     if args.stream_parts:
         args.skip_cpu_baseline = True
         args.skip_selectivity = True
         part_dirs = []
         parts = []
-        stages, manifest, _, stage_s = stream_stages(
+        stages, manifest, _, stage_s, dims = stream_stages(
             os.path.join(args.data_dir, f"rank{rank}"), args.rows, nparts,
             args.msg_len, 1000 * rank + 1, filt, device)
     else:
@@ -338,19 +452,12 @@ def main():
             # ~80 GB box disk): stream parts through the disk instead
             log(f"rank {rank}: disk full ({e}); falling back to "
                 "--stream-parts")
-            import glob
-            import shutil
-            for d in glob.glob(os.path.join(args.data_dir, f"rank{rank}",
-                                            "part_*")):
-                # gen_manifest.json is written last; its absence marks a
-                # partial part stranded by the failed generation
-                if not os.path.exists(os.path.join(d, "gen_manifest.json")):
-                    shutil.rmtree(d, ignore_errors=True)
+            remove_partial_parts(os.path.join(args.data_dir, f"rank{rank}"))
             args.skip_cpu_baseline = True
             args.skip_selectivity = True
             part_dirs = []
             parts = []
-            stages, manifest, _, stage_s = stream_stages(
+            stages, manifest, _, stage_s, dims = stream_stages(
                 os.path.join(args.data_dir, f"rank{rank}"), args.rows, nparts,
                 args.msg_len, 1000 * rank + 1, filt, device)
     staged_bytes = sum(s.staged_bytes for s in stages)
@@ -360,13 +467,14 @@ def main():
     log(f"rank {rank}: staged {staged_bytes / 1e9:.2f} GB "
         f"({rows} rows, {live_rows} live) in {stage_s:.1f}s")
 
+    last_hits = [0] * len(stages)  # what each stage's latest scan() returned
+
     def one_step():
-        hits = 0
         kms = 0.0
-        for s in stages:
-            hits += s.scan()
+        for i, s in enumerate(stages):
+            last_hits[i] = s.scan()
             kms += s.last_kernel_ms
-        return hits, kms
+        return sum(last_hits), kms
 
     # warmup + full-size correctness property (all-match invariant): the
     # headline filters match every generated row by construction, so the
@@ -402,6 +510,14 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        if parts:
+            # one multi-part stage holding every block of every part
+            per_part = [part_dims(p) for p in parts]
+            dims = [(sum(b for b, _ in per_part), sum(w for _, w in per_part))]
+        dump_outputs(args.dump_outputs, stages, dims, last_hits,
+                     suffix=f"_rank{rank}" if distributed else "")
 
     # whole-job aggregation: MAX(elapsed) over ranks; SUM(rows, hits)
     if distributed:

@@ -169,7 +169,7 @@ def test_emu_bench_contract(tmp_path):
                VQL_DATA_DIR=str(tmp_path / "bench_data"))
     r = subprocess.run(
         [sys.executable, "bench.py", "--rows", "200000", "--steps", "2",
-         "--warmup", "1", "--skip-cpu-baseline"],
+         "--warmup", "1", "--full", "--skip-cpu-baseline"],
         env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])

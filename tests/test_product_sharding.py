@@ -105,7 +105,7 @@ def test_bench_distributed_cpu(tmp_path):
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
          "--gpus", "2", "--rows", "200000", "--steps", "2", "--warmup", "1",
-         "--skip-cpu-baseline"],
+         "--full", "--skip-cpu-baseline"],
         env=env, cwd=ROOT, capture_output=True, text=True, timeout=550)
     assert r.returncode == 0, r.stdout[-4000:] + "\n" + r.stderr[-4000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]

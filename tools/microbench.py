@@ -25,15 +25,15 @@ def main():
     ap.add_argument("--msg-len", type=int, default=256)
     ap.add_argument("--steps", type=int, default=6)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--data-dir", default=os.environ.get(
-        "VQL_DATA_DIR", "/tmp/vql_bench_data"))
+    ap.add_argument("--data-dir", default=os.environ.get("VQL_DATA_DIR"))
     args = ap.parse_args()
 
-    from bench import prepare_parts
+    from bench import DEFAULT_DATA_DIR, bench_nparts, prepare_parts
     from victorialogs_amd import Filter, Part, Stage
 
-    nparts = max(1, min(64, (os.cpu_count() or 8),
-                        max(8, args.rows // 16_000_000)))
+    if args.data_dir is None:
+        args.data_dir = DEFAULT_DATA_DIR
+    nparts = bench_nparts(args.rows, 1)
     dirs = prepare_parts(os.path.join(args.data_dir, "rank0"), args.rows,
                          nparts, args.msg_len, seed_base=1)
     parts = [Part(d) for d in dirs]
