@@ -38,6 +38,42 @@ __device__ int64_t g_vl_local_tz_nsecs = 0;
 
 #include "scan_rowops.h"
 
+// Byte pointer into shared memory.  The address space is part of the type so
+// that it survives the __noinline__ tile loops: reads through it are ds_read,
+// not flat loads.
+typedef const __attribute__((address_space(3))) uint8_t* LdsBytePtr;
+
+// TileAcc over an LDS-typed tile pointer (same swizzle).  The tile loops use
+// it instead of TileAcc: through a generic pointer the __noinline__ loops'
+// tile reads compiled to flat loads (flat_load_dwordx4 / flat_load_ubyte),
+// which also wait on the outstanding global loads; typed, they are ds_read.
+struct LdsTileAcc {
+  LdsBytePtr tile;
+  typedef const __attribute__((address_space(3))) uint64_t* LdsU64Ptr;
+  __device__ __forceinline__ long swz(long off) const {
+    return TileAcc{nullptr}.swz(off);
+  }
+  __device__ __forceinline__ uint64_t u64a(long off) const {
+    return *(LdsU64Ptr)(tile + swz(off));
+  }
+  __device__ __forceinline__ void u64a2(long off, uint64_t* x0,
+                                        uint64_t* x1) const {
+    LdsU64Ptr p = (LdsU64Ptr)(tile + swz(off));
+    *x0 = p[0];
+    *x1 = p[1];
+  }
+  __device__ __forceinline__ uint8_t u8(long off) const { return tile[swz(off)]; }
+};
+
+// Cooperative copy of a leaf operand into an LDS operand slot.  Call in
+// workgroup-uniform control flow; a barrier must follow before first use.
+__device__ __forceinline__ void d_fill_operand_slot(uint8_t* slot,
+                                                    const uint8_t* src,
+                                                    uint32_t n, int tid,
+                                                    int bdim) {
+  for (uint32_t k = tid; k < n; k += bdim) slot[k] = src[k];
+}
+
 extern "C" int vql_set_local_tz_nsecs(long long v) {
   int64_t x = v;
   return hipMemcpyToSymbol(HIP_SYMBOL(g_vl_local_tz_nsecs), &x, sizeof(x)) ==
@@ -174,7 +210,7 @@ __device__ __forceinline__ void d_string_tile_loop(
       const long e = uint32_t(__shfl(int(o_lane), lane + 1, 64));
       const long e_fix = uint32_t(lane) == ng - 1 ? long(byte1) : e;
       if (use_tile) {
-        TileAcc a{wtile};
+        LdsTileAcc a{(LdsBytePtr)wtile};
         pred = eval(a, s - byte0, e_fix - s);
       } else {
         GlobalAcc a{col_data};
@@ -199,10 +235,10 @@ __device__ __forceinline__ void d_string_tile_loop(
 // round trip per 64-row group, which is latency-bound when rows are short
 // (a ~30 B-row column moved ~0.8 TB/s vs ~5 TB/s for 256 B rows).  Here a
 // wave fills its tile with SG words' bytes at once (SG = lb.sg, chosen at
-// staging so SG*64*avg_row fits the tile) and evaluates SG ballot words per
-// fill — amortizing the copy latency SG-fold.  Super-groups whose actual
-// byte span overflows the tile (row-length variance) fall back to direct
-// global evaluation for those words, bit-identically.
+// staging from the block's actual super-group spans) and evaluates SG ballot
+// words per fill — amortizing the copy latency SG-fold.  The few super-groups
+// whose byte span overflows the tile (staging caps their number) fall back
+// to direct global evaluation for those words, bit-identically.
 // __noinline__: one clone per evaluator, kept out of the hot per-word loop's
 // instruction stream (see the I-cache regression note above).
 template <bool kOvr, typename EvalFn>
@@ -214,16 +250,24 @@ __device__ __noinline__ void d_string_smallrow_loop(
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   v4u* dst = (v4u*)wtile;
   const uint32_t nsg = (nwords + sgw - 1) / sgw;
+  // Offsets pipeline, as in d_string_tile_loop: o[j] holds word j's
+  // offsets[lane] (clamped to r1), o[8] (lane 0) the super-group's end.  The
+  // next super-group's offsets are loaded while this one's tile is evaluated,
+  // so a fill costs one serialized HBM round trip (the bytes), not two.
+  uint32_t o[9];
+#pragma unroll
+  for (uint32_t j = 0; j < 9; j++) o[j] = 0;
+  if (uint32_t(wave) < nsg) {
+    const uint32_t g0 = r0 + uint32_t(wave) * sgw * 64;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) {
+      if (j < sgw) o[j] = col_offs[min(g0 + j * 64 + uint32_t(lane), r1)];
+    }
+    if (lane == 0) o[8] = col_offs[min(g0 + sgw * 64, r1)];
+  }
   for (uint32_t sg = wave; sg < nsg; sg += nwaves) {
     const uint32_t w0 = sg * sgw;
     const uint32_t g0 = r0 + w0 * 64;
-    uint32_t o[9];
-#pragma unroll
-    for (uint32_t j = 0; j < 8; j++) {
-      o[j] = j < sgw ? col_offs[min(g0 + j * 64 + uint32_t(lane), r1)] : 0;
-    }
-    o[8] = 0;
-    if (lane == 0) o[8] = col_offs[min(g0 + sgw * 64, r1)];
     const uint32_t byte0 =
         uint32_t(__builtin_amdgcn_readfirstlane(int(o[0]))) & ~15u;
     const uint32_t byte1 = uint32_t(__shfl(int(o[8]), 0, 64));
@@ -259,6 +303,22 @@ __device__ __noinline__ void d_string_smallrow_loop(
         dst[(k + 192) ^ (((k + 192) >> 4) & 15)] = a3;
       }
       for (; k < n16; k += 64) dst[k ^ ((k >> 4) & 15)] = src[k];
+    }
+    // prefetch the next super-group's offsets behind the copy
+    uint32_t o_next[9];
+#pragma unroll
+    for (uint32_t j = 0; j < 9; j++) o_next[j] = 0;
+    if (sg + nwaves < nsg) {
+      const uint32_t gn = r0 + (sg + nwaves) * sgw * 64;
+#pragma unroll
+      for (uint32_t j = 0; j < 8; j++) {
+        if (j < sgw) {
+          o_next[j] = col_offs[min(gn + j * 64 + uint32_t(lane), r1)];
+        }
+      }
+      if (lane == 0) o_next[8] = col_offs[min(gn + sgw * 64, r1)];
+    }
+    if (use_tile) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
 #pragma unroll
@@ -280,7 +340,7 @@ __device__ __noinline__ void d_string_smallrow_loop(
         const long s = o[j];
         const long e = uint32_t(lane) == ng - 1 ? long(wend) : long(e0);
         if (use_tile) {
-          TileAcc a{wtile};
+          LdsTileAcc a{(LdsBytePtr)wtile};
           pred = eval(a, s - byte0, e - s);
         } else {
           GlobalAcc a{col_data};
@@ -294,6 +354,8 @@ __device__ __noinline__ void d_string_smallrow_loop(
       }
       if (lane == 0) out[w] = word;
     }
+#pragma unroll
+    for (uint32_t j = 0; j < 9; j++) o[j] = o_next[j];
   }
 }
 
@@ -301,12 +363,13 @@ __device__ __noinline__ void d_string_smallrow_loop(
 // evaluate from one tile fill, halving the column's HBM reads (an OR/AND of
 // two phrases on one column — configs[3]'s or8 — otherwise streams the
 // column once per leaf).  Same structure as d_string_tile_loop; the copy is
-// shared, the two matchers run back-to-back from LDS.
+// shared, the two matchers run back-to-back from LDS.  Both phrases are read
+// from the LDS operand slots.
 __device__ __noinline__ void d_string_phrase2_loop(
     const uint8_t* __restrict__ col_data, const uint32_t* __restrict__ col_offs,
     uint8_t* wtile, uint64_t* out1, uint64_t* out2, uint32_t r0, uint32_t r1,
-    uint32_t nwords, int lane, int wave, int nwaves, const uint8_t* p1,
-    uint32_t n1, uint8_t f1, const uint8_t* p2, uint32_t n2, uint8_t f2) {
+    uint32_t nwords, int lane, int wave, int nwaves, LdsBytePtr p1,
+    uint32_t n1, uint8_t f1, LdsBytePtr p2, uint32_t n2, uint8_t f2) {
   typedef uint32_t v4u __attribute__((ext_vector_type(4)));
   v4u* dst = (v4u*)wtile;
   uint32_t wd = wave;
@@ -370,7 +433,7 @@ __device__ __noinline__ void d_string_phrase2_loop(
       const long e = uint32_t(__shfl(int(o_lane), lane + 1, 64));
       const long e_fix = uint32_t(lane) == ng - 1 ? long(byte1) : e;
       if (use_tile) {
-        TileAcc a{wtile};
+        LdsTileAcc a{(LdsBytePtr)wtile};
         pred1 = d_match_phrase_at(a, s - byte0, e_fix - s, p1, n1, f1);
         pred2 = d_match_phrase_at(a, s - byte0, e_fix - s, p2, n2, f2);
       } else {
@@ -396,6 +459,9 @@ __device__ __forceinline__ bool d_bloom_gate_ok(const DevLeafBlock& lb,
                                                 int tid, int bdim,
                                                 int* shared_flag) {
   if (!lb.nhashes) return true;
+  // back-to-back gates share the flag: every wave must have read the
+  // previous gate's verdict before thread 0 resets it
+  __syncthreads();
   if (tid == 0) *shared_flag = 1;
   __syncthreads();
   if (lb.bloom_words > 0) {
@@ -421,6 +487,11 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
   __shared__ __attribute__((aligned(16))) uint8_t tile[kNumWaves * kWaveTileBytes];
   __shared__ int bloom_ok;
   __shared__ unsigned long long wave_sums[4];
+  // LDS operand cache: the leaf's pattern bytes are constant for the whole
+  // launch, and reading them from global memory put one dependent vector
+  // memory round trip per pattern byte into the candidate verify loop.
+  // Slot 0 serves a single leaf, slot 1 the second leaf of a fused pair.
+  __shared__ __attribute__((aligned(16))) uint8_t opnd[2][kOperandSlotBytes];
 
   const DevChunk ck = chunks[blockIdx.x];
   const DevBlock blk = blocks[ck.block];
@@ -431,6 +502,8 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
   const int lane = tid & 63;
   const int wave = tid >> 6;
   const int nwaves = blockDim.x >> 6;
+  const LdsBytePtr opnd0 = (LdsBytePtr)&opnd[0][0];
+  const LdsBytePtr opnd1 = (LdsBytePtr)&opnd[1][0];
 
   int sp = 0;
   for (int i = 0; i < nops; i++) {
@@ -449,15 +522,24 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
         const DevLeafBlock& lb2 =
             lbs[size_t(ck.block) * nleaves + ops[i + 1].leaf];
         if (lb2.kind == kScanPhraseStr && lb2.mode == kModeScan &&
-            lb2.data == lb.data && lb2.offsets == lb.offsets) {
+            lb2.data == lb.data && lb2.offsets == lb.offsets &&
+            lb.operand_len <= kOperandSlotBytes &&
+            lb2.operand_len <= kOperandSlotBytes) {
+          // both operands go to LDS (nobody reads the slots between the
+          // top-of-op barrier and the one below)
+          d_fill_operand_slot(opnd[0], lb.operand, lb.operand_len, tid,
+                              blockDim.x);
+          d_fill_operand_slot(opnd[1], lb2.operand, lb2.operand_len, tid,
+                              blockDim.x);
           const bool ok1 = d_bloom_gate_ok(lb, tid, blockDim.x, &bloom_ok);
           const bool ok2 = d_bloom_gate_ok(lb2, tid, blockDim.x, &bloom_ok);
+          __syncthreads();  // slots visible even when neither leaf has a gate
           if (ok1 && ok2) {
             d_string_phrase2_loop(lb.data, lb.offsets,
                                   tile + wave * kWaveTileBytes, stack[sp],
                                   stack[sp + 1], r0, r1, nwords, lane, wave,
-                                  nwaves, lb.operand, lb.operand_len, lb.flags,
-                                  lb2.operand, lb2.operand_len, lb2.flags);
+                                  nwaves, opnd0, lb.operand_len, lb.flags,
+                                  opnd1, lb2.operand_len, lb2.flags);
             sp += 2;
             i++;
             continue;
@@ -470,8 +552,39 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
         sp++;
         continue;
       }
-      // bloom gate (bloomfilter.go:173-191), cooperative over the workgroup
-      if (lb.nhashes) {
+      // Operand to LDS slot 0: a phrase that fits the slot, or a literal
+      // regexp.  The blob header decode is uniform and done once per leaf: a
+      // single-branch blob (no alt-list marker) whose class is only_prefix
+      // (not NFA, not always-true) computes d_index_at(prefix) >= 0, which
+      // is d_match_phrase_at with flags 0 and a non-empty pattern, so it
+      // takes the phrase clone.
+      bool lds_phrase = false;
+      uint32_t lds_len = 0;
+      uint8_t lds_flags = 0;
+      if (lb.kind == kScanPhraseStr) {
+        if (lb.operand_len <= kOperandSlotBytes) {
+          lds_phrase = true;
+          lds_len = lb.operand_len;
+          lds_flags = lb.flags;
+          d_fill_operand_slot(opnd[0], lb.operand, lds_len, tid, blockDim.x);
+        }
+      } else if (lb.kind == kScanRegexStr) {
+        const uint8_t* blob = lb.operand;
+        const uint8_t re_flags = blob[0];
+        if ((re_flags & kReOnlyPrefix) && !(re_flags & (kReNfa | kReAlways))) {
+          const uint32_t plen = uint32_t(blob[1]) | uint32_t(blob[2]) << 8;
+          if (plen >= 1 && plen <= kOperandSlotBytes) {
+            lds_phrase = true;
+            lds_len = plen;
+            d_fill_operand_slot(opnd[0], blob + 7, plen, tid, blockDim.x);
+          }
+        }
+      }
+      // bloom gate (bloomfilter.go:173-191), cooperative over the workgroup;
+      // its barriers also publish the operand slot
+      if (!lb.nhashes) {
+        if (lds_phrase) __syncthreads();
+      } else {
         if (tid == 0) bloom_ok = 1;
         __syncthreads();
         if (lb.bloom_words > 0) {
@@ -496,13 +609,12 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
         const uint8_t* col_data = lb.data;
         const uint32_t* col_offs = lb.offsets;
         const uint8_t* op_ptr = lb.operand;
-        const uint32_t op_len = lb.operand_len;
-        const uint8_t op_flags = lb.flags;
         const uint32_t sgw = lb.sg;
-        if (lb.kind == kScanPhraseStr) {
-          // hot clone: only the phrase matcher in the loop body
+        if (lds_phrase) {
+          // hot clone: only the phrase matcher in the loop body, pattern in
+          // LDS (phrase leaves and literal regexps)
           auto eval = [=](const auto& a, long s0, long sn) {
-            return d_match_phrase_at(a, s0, sn, op_ptr, op_len, op_flags);
+            return d_match_phrase_at(a, s0, sn, opnd0, lds_len, lds_flags);
           };
           if (sgw > 1) {
             d_string_smallrow_loop<false>(col_data, col_offs, nullptr, nullptr,
@@ -528,6 +640,8 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
                                       nwaves, eval);
           }
         } else {
+          // generic clone, operand in global memory (also a phrase longer
+          // than the LDS operand slot)
           const bool anycase = lb.kind == kScanAnyCasePhraseStr ||
                                lb.kind == kScanAnyCasePrefixStr;
           auto eval = [&](const auto& a, long s0, long sn) {

@@ -157,7 +157,7 @@ __device__ uint32_t d_utf8_decode_last(const A& a, long off, long n, int* size) 
 }
 
 // strings.Index over accessor bytes [s0, s0+sn): first occurrence of the
-// operand (global memory, byte-addressable) or -1.  SWAR scan over ALIGNED
+// operand (byte-addressable, global memory or LDS) or -1.  SWAR scan over ALIGNED
 // u64 windows with a TWO-byte anchor (first byte at k AND second byte at
 // k+1; the window's top byte keeps its candidate bit since its successor
 // lives in the next window) — a first-byte-only anchor left ~6 candidate
@@ -173,9 +173,13 @@ __device__ __forceinline__ uint64_t d_swar_zero(uint64_t t) {
 // the hot clone's codegen (same class as the round-1 descriptor-reload
 // regression).  The byte loop below stays.
 
-template <typename A>
-__device__ long d_index_at(const A& a, long s0, long sn, const uint8_t* sub,
-                           long subn) {
+// P is the operand's pointer type: `const uint8_t*` for operands in global
+// memory, or the kernel's LDS byte pointer for a leaf operand cached in
+// shared memory (the type keeps the address space visible through the
+// __noinline__ tile loops, so the verify loop's pattern byte is an LDS read
+// instead of a dependent global round trip per byte).
+template <typename A, typename P>
+__device__ long d_index_at(const A& a, long s0, long sn, P sub, long subn) {
   if (subn == 0) return 0;
   if (subn > sn) return -1;
   const uint8_t c0 = sub[0];
@@ -253,8 +257,8 @@ __device__ long d_index_at(const A& a, long s0, long sn, const uint8_t* sub,
 
 // getPhrasePos (filter_phrase.go:220-270) over accessor bytes [s0, s0+sn);
 // returns the match position or -1.
-template <typename A>
-__device__ long d_get_phrase_pos_at(const A& a, long s0, long sn, const uint8_t* ph,
+template <typename A, typename P>
+__device__ long d_get_phrase_pos_at(const A& a, long s0, long sn, P ph,
                                     long phn, uint8_t flags) {
   if (phn == 0) return 0;
   if (phn > sn) return -1;
@@ -289,9 +293,9 @@ __device__ long d_get_phrase_pos_at(const A& a, long s0, long sn, const uint8_t*
   }
 }
 
-template <typename A>
+template <typename A, typename P>
 __device__ __forceinline__ bool d_match_phrase_at(const A& a, long s0, long sn,
-                                                  const uint8_t* ph, long phn,
+                                                  P ph, long phn,
                                                   uint8_t flags) {
   if (phn == 0) return sn == 0;  // filter_phrase.go:212-215
   return d_get_phrase_pos_at(a, s0, sn, ph, phn, flags) >= 0;

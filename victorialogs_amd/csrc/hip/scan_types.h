@@ -20,6 +20,11 @@ constexpr uint32_t kChunkWords = kChunkRows / 64;
 // small-row super-group size (DevLeafBlock.sg).
 constexpr uint32_t kWaveTileBytes = 17408;
 constexpr uint32_t kNumWaves = 4;
+// LDS operand cache of the scan kernel: a phrase operand (or a literal
+// regexp's prefix) of up to this many bytes is copied to shared memory once
+// per chunk and matched from there; longer operands stay in global memory.
+// Two slots (the second serves the phrase-pair fusion path).
+constexpr uint32_t kOperandSlotBytes = 512;
 constexpr int kMaxProgOps = 64;
 constexpr int kMaxStackDepth = 8;
 

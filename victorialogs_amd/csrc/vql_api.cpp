@@ -12,6 +12,7 @@
 // HIP device and fails loudly otherwise.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -270,7 +271,34 @@ struct StagedStrCol {
   const uint32_t* d_offsets = nullptr;
   uint64_t data_bytes = 0;
   uint64_t rows = 0;
+  uint32_t sg = 1;  // small-row super-group size (DevLeafBlock.sg)
 };
+
+// Small-row super-group size for a string column: the largest sg in {8,4,2}
+// for which the block's ACTUAL super-group byte spans (sg*64 rows counted
+// from row 0, start rounded down to the tile copy's 16-byte alignment) fit
+// one wave tile, allowing at most max(1, nsg/32) overflowing super-groups —
+// those take the kernel's per-super-group global fallback, bit-identically.
+// 1 = per-word tile loop.
+static uint32_t pick_super_group(const std::vector<uint32_t>& offs,
+                                 uint64_t rows) {
+  if (rows == 0 || offs.size() < rows + 1) return 1;
+  const uint64_t nwords = (rows + 63) / 64;
+  for (uint32_t sg = 8; sg >= 2; sg /= 2) {
+    const uint64_t nsg = (nwords + sg - 1) / sg;
+    const uint64_t cap = std::max<uint64_t>(1, nsg / 32);
+    uint64_t over = 0;
+    for (uint64_t g = 0; g < nsg && over <= cap; g++) {
+      const uint64_t ra = g * sg * 64;
+      const uint64_t rb = std::min<uint64_t>(rows, ra + uint64_t(sg) * 64);
+      const uint64_t span = uint64_t(offs[rb]) - (uint64_t(offs[ra]) & ~15ull);
+      if (span > kWaveTileBytes) over++;
+    }
+    if (over <= cap) return sg;
+  }
+  return 1;
+}
+
 struct StagedBloom {
   const uint64_t* d_words = nullptr;
   uint32_t nwords = 0;
@@ -304,6 +332,7 @@ struct BlockStageCtx {
       sc.d_offsets = (const uint32_t*)st->push(dec.offsets.data(),
                                                dec.offsets.size() * 4, 4);
       sc.data_bytes = dec.data.size();
+      sc.sg = pick_super_group(dec.offsets, sc.rows);
     }
     return cols.emplace(ch.name, std::move(sc)).first->second;
   }
@@ -2550,19 +2579,8 @@ Stage* build_stage_refs(std::vector<std::pair<VqlPart*, long>> refs,
           case kScanAnyCasePrefixStr: {
             const StagedStrCol& sc = ctx.cols.at(leaf_infos[size_t(l)].cname);
             block_algo += sc.data_bytes + (bh.rows_count + 1) * 4;
-            // small-row super-group size: how many 64-row bitmap words fit
-            // one wave tile with margin for row-length variance (the kernel
-            // falls back per super-group when the actual span overflows)
-            if (sc.rows > 0) {
-              const uint64_t avg = sc.data_bytes / sc.rows;
-              uint32_t sgw = 1;
-              while (sgw < 8 &&
-                     uint64_t(sgw) * 2 * 64 * (avg + 8) + 2048 <=
-                         kWaveTileBytes) {
-                sgw *= 2;
-              }
-              lb.sg = sgw;
-            }
+            // small-row super-group size, from the block's actual spans
+            if (sc.rows > 0) lb.sg = sc.sg;
             break;
           }
           case kScanDict:
