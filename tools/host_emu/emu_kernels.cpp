@@ -1,7 +1,7 @@
 // Serial CPU emulation of the scan/gather/bloom kernels over the SAME
 // per-row device code (scan_rowops.h) and the same descriptor layouts.
 // Mirrors scan_program_kernel's semantics (postfix program over per-block
-// bitmap words, bloom gates, any-case overrides, tail masking).
+// bitmap words, any-case overrides, tail masking).
 // TEST INFRASTRUCTURE — loaded via VQL_LIB by tests/test_emu_pipeline.py.
 #include <cmath>
 #include <cstdint>
@@ -83,25 +83,11 @@ extern "C" hipError_t vql_launch_scan(const DevOp* ops, int nops,
         if (lb.mode == kModeAll) {
           std::fill(out.begin(), out.end(), ~uint64_t(0));
         } else if (lb.mode == kModeScan) {
-          bool bloom_ok = true;
-          if (lb.nhashes && lb.bloom_words > 0 &&
-              lb.kind != kScanAnyCasePhraseStr &&
-              lb.kind != kScanAnyCasePrefixStr) {
-            const uint64_t max_bits = uint64_t(lb.bloom_words) * 64;
-            for (uint32_t k = 0; k < lb.nhashes; k++) {
-              uint64_t idx = lb.hashes[k] % max_bits;
-              if (((lb.bloom[idx >> 6] >> (idx & 63)) & 1) == 0) {
-                bloom_ok = false;
-                break;
-              }
-            }
-          }
-          if (bloom_ok) {
-            for (uint32_t w = 0; w < nwords; w++) {
-              const uint32_t g0 = r0 + w * 64;
-              const uint32_t g1 = g0 + 64 < r1 ? g0 + 64 : r1;
-              emu_eval_leaf_word(lb, g0, g1, &out[w]);
-            }
+          // bloom gates are decided at staging (a miss is kModeNone)
+          for (uint32_t w = 0; w < nwords; w++) {
+            const uint32_t g0 = r0 + w * 64;
+            const uint32_t g1 = g0 + 64 < r1 ? g0 + 64 : r1;
+            emu_eval_leaf_word(lb, g0, g1, &out[w]);
           }
         }
         stack.push_back(std::move(out));

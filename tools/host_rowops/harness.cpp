@@ -40,7 +40,43 @@ __attribute__((constructor)) static void rowops_tz_init() {
   vl::g_vl_local_tz_nsecs = vl::local_tz_offset_nsecs();
 }
 
+// BufAcc whose byte reads are checked against the row [lo, hi): d_index_at's
+// verify may read no byte outside the row (the SWAR scan's u64 windows are
+// allowed their over-read and are not checked).
+struct CheckedAcc {
+  const uint8_t* base;
+  long lo, hi;
+  bool* out_of_row;
+  uint64_t u64a(long off) const { return BufAcc{base}.u64a(off); }
+  void u64a2(long off, uint64_t* x0, uint64_t* x1) const {
+    BufAcc{base}.u64a2(off, x0, x1);
+  }
+  uint8_t u8(long off) const {
+    if (off < lo || off >= hi) {
+      *out_of_row = true;
+      return 0;
+    }
+    return base[off];
+  }
+};
+
 extern "C" {
+
+// d_index_at over a row placed `align` (0..15) bytes into a 16-byte-aligned,
+// padded buffer.  Returns what d_index_at returns, or -2 if any byte read of
+// the verify fell outside the row.
+long h_dev_index_checked(const char* s, long sn, long align, const char* sub,
+                         long subn) {
+  const long s0 = 16 + (align & 15);
+  std::vector<uint8_t> store(size_t(s0 + sn + 64 + 16), 0xA5);
+  uint8_t* buf = store.data();
+  buf += (16 - (uintptr_t(buf) & 15)) & 15;
+  if (sn > 0) memcpy(buf + s0, s, size_t(sn));
+  bool out_of_row = false;
+  CheckedAcc a{buf, s0, s0 + sn, &out_of_row};
+  const long r = d_index_at(a, s0, sn, (const uint8_t*)sub, subn);
+  return out_of_row ? -2 : r;
+}
 
 // device-code entry points over a plain byte buffer (BufAcc semantics)
 long h_dev_phrase_pos(const char* s, long sn, const char* ph, long pn) {

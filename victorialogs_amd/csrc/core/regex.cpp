@@ -624,7 +624,22 @@ void collect_literals(const RNode& raw, std::vector<std::string>& out) {
     return;
   }
   if (n->kind != RNode::Concat) return;
+  // The raw tree holds one Lit per rune where Go's parser holds one
+  // OpLiteral per run of adjacent runes: join the runs, or no literal ever
+  // keeps a token after skipFirstLastToken and regexp leaves get no bloom
+  // gate.  A group ends a run, as it does in Go's tree.
+  bool run = false;
   for (const auto& sub : n->subs) {
+    if (sub.kind == RNode::Lit) {
+      if (run) {
+        out.back() += sub.lit;
+      } else {
+        out.push_back(sub.lit);
+      }
+      run = true;
+      continue;
+    }
+    run = false;
     const RNode* s = &sub;
     while (s->kind == RNode::Group) s = &s->subs[0];
     if (s->kind == RNode::Lit) out.push_back(s->lit);

@@ -5,8 +5,8 @@
 // predicates are computed lane-per-row and assembled into bitmap words with
 // 64-lane ballots (one wavefront ballot = one u64 bitmap word covering 64
 // consecutive rows, LSB-first — exactly the bitmap.go:113-125 layout the
-// drop-in boundary requires).  Bloom gates (bloomfilter.go:173-191) run
-// cooperatively per chunk before any row is touched.
+// drop-in boundary requires).  Bloom gates (bloomfilter.go:173-191) are
+// decided on the host at staging; the kernel never sees a gated leaf.
 //
 // String columns are scanned through an LDS tile: 256-row groups are copied
 // from HBM with coalesced 16-byte loads (streaming reads == algorithmic
@@ -36,12 +36,20 @@ namespace vl {
 // host local timezone offset for no-suffix RFC3339 parses (see scan_rowops.h)
 __device__ int64_t g_vl_local_tz_nsecs = 0;
 
-#include "scan_rowops.h"
-
 // Byte pointer into shared memory.  The address space is part of the type so
 // that it survives the __noinline__ tile loops: reads through it are ds_read,
 // not flat loads.
 typedef const __attribute__((address_space(3))) uint8_t* LdsBytePtr;
+
+// d_verify_at's operand read for the LDS operand slot: the slot is 16-byte
+// aligned and the verify asks at i % 4 == 0 with i + 4 <= operand length, so
+// one aligned ds_read_b32 serves four pattern bytes.  Declared before
+// scan_rowops.h so that the verify template sees it.
+__device__ __forceinline__ uint32_t d_operand4(LdsBytePtr sub, long i) {
+  return *(const __attribute__((address_space(3))) uint32_t*)(sub + i);
+}
+
+#include "scan_rowops.h"
 
 // TileAcc over an LDS-typed tile pointer (same swizzle).  The tile loops use
 // it instead of TileAcc: through a generic pointer the __noinline__ loops'
@@ -454,29 +462,6 @@ __device__ __noinline__ void d_string_phrase2_loop(
   }
 }
 
-// Cooperative bloom gate (bloomfilter.go:173-191); uniform control flow.
-__device__ __forceinline__ bool d_bloom_gate_ok(const DevLeafBlock& lb,
-                                                int tid, int bdim,
-                                                int* shared_flag) {
-  if (!lb.nhashes) return true;
-  // back-to-back gates share the flag: every wave must have read the
-  // previous gate's verdict before thread 0 resets it
-  __syncthreads();
-  if (tid == 0) *shared_flag = 1;
-  __syncthreads();
-  if (lb.bloom_words > 0) {
-    const uint64_t max_bits = uint64_t(lb.bloom_words) * 64;
-    bool miss = false;
-    for (uint32_t k = tid; k < lb.nhashes; k += bdim) {
-      uint64_t idx = lb.hashes[k] % max_bits;
-      if (((lb.bloom[idx >> 6] >> (idx & 63)) & 1) == 0) miss = true;
-    }
-    if (miss) *shared_flag = 0;
-  }
-  __syncthreads();
-  return *shared_flag != 0;
-}
-
 // ---- the program kernel ----
 
 __global__ __launch_bounds__(256) void scan_program_kernel(
@@ -485,7 +470,6 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
     const DevChunk* __restrict__ chunks, unsigned long long* __restrict__ hits) {
   __shared__ uint64_t stack[kMaxStackDepth][kChunkWords];
   __shared__ __attribute__((aligned(16))) uint8_t tile[kNumWaves * kWaveTileBytes];
-  __shared__ int bloom_ok;
   __shared__ unsigned long long wave_sums[4];
   // LDS operand cache: the leaf's pattern bytes are constant for the whole
   // launch, and reading them from global memory put one dependent vector
@@ -514,8 +498,8 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
       uint64_t* out = stack[sp];
       // phrase-pair fusion: the next op is another phrase leaf over the
       // SAME column -> evaluate both from one tile fill (halves this
-      // column's HBM reads).  Falls through to the single path when a
-      // bloom gate misses (rare; the single path re-evaluates it).
+      // column's HBM reads).  A leaf whose bloom gate missed at staging is
+      // kModeNone and takes the single path.
       if (i + 1 < nops && ops[i + 1].kind == kOpLeaf &&
           lb.kind == kScanPhraseStr && lb.mode == kModeScan && lb.sg <= 1 &&
           sp + 1 < kMaxStackDepth) {
@@ -531,19 +515,15 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
                               blockDim.x);
           d_fill_operand_slot(opnd[1], lb2.operand, lb2.operand_len, tid,
                               blockDim.x);
-          const bool ok1 = d_bloom_gate_ok(lb, tid, blockDim.x, &bloom_ok);
-          const bool ok2 = d_bloom_gate_ok(lb2, tid, blockDim.x, &bloom_ok);
-          __syncthreads();  // slots visible even when neither leaf has a gate
-          if (ok1 && ok2) {
-            d_string_phrase2_loop(lb.data, lb.offsets,
-                                  tile + wave * kWaveTileBytes, stack[sp],
-                                  stack[sp + 1], r0, r1, nwords, lane, wave,
-                                  nwaves, opnd0, lb.operand_len, lb.flags,
-                                  opnd1, lb2.operand_len, lb2.flags);
-            sp += 2;
-            i++;
-            continue;
-          }
+          __syncthreads();  // publishes both slots
+          d_string_phrase2_loop(lb.data, lb.offsets,
+                                tile + wave * kWaveTileBytes, stack[sp],
+                                stack[sp + 1], r0, r1, nwords, lane, wave,
+                                nwaves, opnd0, lb.operand_len, lb.flags,
+                                opnd1, lb2.operand_len, lb2.flags);
+          sp += 2;
+          i++;
+          continue;
         }
       }
       if (lb.mode == kModeNone || lb.mode == kModeAll) {
@@ -580,29 +560,9 @@ __global__ __launch_bounds__(256) void scan_program_kernel(
           }
         }
       }
-      // bloom gate (bloomfilter.go:173-191), cooperative over the workgroup;
-      // its barriers also publish the operand slot
-      if (!lb.nhashes) {
-        if (lds_phrase) __syncthreads();
-      } else {
-        if (tid == 0) bloom_ok = 1;
-        __syncthreads();
-        if (lb.bloom_words > 0) {
-          const uint64_t max_bits = uint64_t(lb.bloom_words) * 64;
-          bool miss = false;
-          for (uint32_t k = tid; k < lb.nhashes; k += blockDim.x) {
-            uint64_t idx = lb.hashes[k] % max_bits;
-            if (((lb.bloom[idx >> 6] >> (idx & 63)) & 1) == 0) miss = true;
-          }
-          if (miss) bloom_ok = 0;
-        }
-        __syncthreads();
-        if (!bloom_ok) {
-          for (uint32_t w = tid; w < nwords; w += blockDim.x) out[w] = 0;
-          sp++;
-          continue;
-        }
-      }
+      // the one barrier that publishes the operand slot before the tile loop
+      // (bloom gates, bloomfilter.go:173-191, are decided at staging)
+      if (lds_phrase) __syncthreads();
 
       if (d_is_string_kind(lb.kind)) {
         uint8_t* wtile = tile + wave * kWaveTileBytes;

@@ -171,13 +171,63 @@ __device__ __forceinline__ uint64_t d_swar_zero(uint64_t t) {
 // aligned u64-window compares regressed EVERY config (headline 11.7 -> 9.2
 // G rows/s, non-matching 10.5 -> 18.4 ms) — the extra live values collapse
 // the hot clone's codegen (same class as the round-1 descriptor-reload
-// regression).  The byte loop below stays.
+// regression).  The verify keeps byte loads (d_verify_at below); it only
+// groups them.
+
+// Candidate verify, kVerifyGroup bytes per step: the byte loads of a group
+// (still byte loads, tile side and operand side) are issued together and
+// compared together, with one early exit per group.  The byte-at-a-time loop
+// put two dependent LDS round trips per pattern byte on every lane's serial
+// chain.  The remainder (< kVerifyGroup bytes) is one more group whose byte
+// indices are clamped to the last pattern byte, so it reads nothing outside
+// [pos, pos+subn) of the row or [0, subn) of the operand.
+#ifndef VL_VERIFY_GROUP
+#define VL_VERIFY_GROUP 4
+#endif
+constexpr int kVerifyGroup = VL_VERIFY_GROUP;
+static_assert(kVerifyGroup == 4 || kVerifyGroup == 8, "verify group width");
+
+// Operand bytes [i, i+4), little-endian packed.  Byte reads for any pointer
+// type; scan_kernels.hip overloads it for the LDS operand slot (i % 4 == 0
+// there, one aligned 4-byte read).
+template <typename P>
+__device__ __forceinline__ uint32_t d_operand4(P sub, long i) {
+  return uint32_t(sub[i]) | uint32_t(sub[i + 1]) << 8 |
+         uint32_t(sub[i + 2]) << 16 | uint32_t(sub[i + 3]) << 24;
+}
+
+template <typename A, typename P>
+__device__ __forceinline__ bool d_verify_at(const A& a, long pos, P sub,
+                                            long subn) {
+  long i = 0;
+  for (; i + kVerifyGroup <= subn; i += kVerifyGroup) {
+    uint32_t diff = 0;
+    for (int g = 0; g < kVerifyGroup; g += 4) {
+      const uint32_t t = uint32_t(a.u8(pos + i + g)) |
+                         uint32_t(a.u8(pos + i + g + 1)) << 8 |
+                         uint32_t(a.u8(pos + i + g + 2)) << 16 |
+                         uint32_t(a.u8(pos + i + g + 3)) << 24;
+      diff |= t ^ d_operand4(sub, i + g);
+    }
+    if (diff) return false;
+  }
+  const long rem = subn - i;
+  if (rem > 0) {
+    uint32_t diff = 0;
+    for (int k = 0; k < kVerifyGroup - 1; k++) {
+      const long j = i + (k < rem ? k : rem - 1);
+      diff |= uint32_t(a.u8(pos + j)) ^ uint32_t(sub[j]);
+    }
+    if (diff) return false;
+  }
+  return true;
+}
 
 // P is the operand's pointer type: `const uint8_t*` for operands in global
 // memory, or the kernel's LDS byte pointer for a leaf operand cached in
 // shared memory (the type keeps the address space visible through the
-// __noinline__ tile loops, so the verify loop's pattern byte is an LDS read
-// instead of a dependent global round trip per byte).
+// __noinline__ tile loops, so the verify's pattern bytes are LDS reads
+// instead of dependent global round trips).
 template <typename A, typename P>
 __device__ long d_index_at(const A& a, long s0, long sn, P sub, long subn) {
   if (subn == 0) return 0;
@@ -242,14 +292,7 @@ __device__ long d_index_at(const A& a, long s0, long sn, P sub, long subn) {
       if (pos > last) return -1;
       // verify from byte 0: the SWAR zero-scan's borrow cascade can flag a
       // byte equal to c0^1 right after a true candidate ("101" vs "11")
-      bool eq = true;
-      for (long i = 0; i < subn; i++) {
-        if (a.u8(pos + i) != sub[i]) {
-          eq = false;
-          break;
-        }
-      }
-      if (eq) return pos - s0;
+      if (d_verify_at(a, pos, sub, subn)) return pos - s0;
     }
   }
   return -1;

@@ -76,7 +76,7 @@ enum ScanKind : uint8_t {
   kScanAnyCasePhraseStr = 38,  // matchAnyCasePhrase, ASCII rows (filter_any_case_phrase.go:159-181)
   kScanAnyCasePrefixStr = 39,  // matchAnyCasePrefix, ASCII rows (filter_any_case_prefix.go:161-183)
   // two-column filters (filter_eq_field.go, filter_le_field.go); side B's
-  // data/offsets ride in the unused bloom-gate fields hashes/bloom
+  // data/offsets ride in the side-data fields hashes/bloom
   kScanEqFieldBin = 40,     // fixed-width encoded equality
   kScanEqFieldDict = 41,    // dict codes vs 8x8 equality matrix in vmin
   kScanLeFieldDict = 42,    // dict codes vs 8x8 le matrix in vmin
@@ -116,18 +116,19 @@ struct DevLeafBlock {
   uint8_t kind;
   uint8_t width;  // fixed-width kinds: 1/2/4/8
   uint8_t flags;
-  // bloom gate probe hashes; 0 = no gate.  The any-case string kinds carry
-  // no bloom gate and reuse `hashes`/`bloom` as the host-resolved override
-  // bitmaps instead (rows with non-ASCII bytes: bit set in hashes=>ovr_mask
-  // means the row result is the bloom=>ovr_val bit) — keeps the descriptor
-  // at 96 B, which the hot scan loop is sensitive to.
-  uint32_t nhashes;
-  uint32_t bloom_words;
+  // Bloom gates are decided at staging (a miss stages the leaf as kModeNone),
+  // so the kernel sees no gate.  `hashes`/`bloom` keep their names from the
+  // device gate and carry per-kind side data: the any-case string kinds use
+  // them as the host-resolved override bitmaps (rows with non-ASCII bytes:
+  // bit set in hashes=>ovr_mask means the row result is the bloom=>ovr_val
+  // bit), the two-column kinds as side B's data/offsets.  The pad keeps the
+  // descriptor at 96 B, which the hot scan loop is sensitive to.
+  uint32_t pad_[2];
   uint32_t dict_mask;      // kScanDict: bit i set if dict value i matches
   uint32_t operand_len;
   uint32_t sg;             // string kinds: words per tile fill (2/4/8) for
                            // the small-row loop; 0/1 = per-word tile loop
-  const uint64_t* hashes;  // device ptrs
+  const uint64_t* hashes;  // device ptrs; per-kind side data (see above)
   const uint64_t* bloom;
   const uint8_t* operand;  // phrase bytes / bin value / serialized regex
   const uint8_t* data;     // column payload (bytes / fixed-width / codes)

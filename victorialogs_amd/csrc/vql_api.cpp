@@ -134,9 +134,8 @@ struct LeafInfo {
   std::string cname;          // canonical column name
   bytes operand;              // phrase/value bytes or regex blob
   uint8_t phrase_flags = 0;
-  // device pointers (filled at stage time)
+  // device pointer (filled at stage time)
   const uint8_t* d_operand = nullptr;
-  const uint64_t* d_hashes = nullptr;
 };
 
 struct Stage {
@@ -299,20 +298,20 @@ static uint32_t pick_super_group(const std::vector<uint32_t>& offs,
   return 1;
 }
 
-struct StagedBloom {
-  const uint64_t* d_words = nullptr;
-  uint32_t nwords = 0;
-};
-
 struct BlockStageCtx {
   Stage* st;
   const PartReader* pr;
   const BlockHeader* bh;
   PartReader::BlockColumns bc;
   std::map<std::string, StagedStrCol> cols;
-  std::map<std::string, StagedBloom> blooms;
   std::map<std::string, std::vector<uint64_t>> host_blooms;
   const int64_t* d_ts = nullptr;
+  // the column the leaf being staged uploaded itself (if has_fresh; _msg is
+  // stored under the empty name), and the arena as it was before: a
+  // bloom-gate miss takes the upload back
+  bool has_fresh = false;
+  std::string fresh_col;
+  Stage::ArenaMark fresh_mark{};
 
   const StagedStrCol& stage_column(const ColumnHeader& ch) {
     auto it = cols.find(ch.name);
@@ -325,6 +324,9 @@ struct BlockStageCtx {
       sc.is_const = true;
       sc.const_value.assign((const char*)dec.data.data(), dec.data.size());
     } else {
+      has_fresh = true;
+      fresh_col = ch.name;
+      fresh_mark = st->mark();
       sc.d_data = st->push(dec.data.data(), dec.data.size());
       // the tile copy rounds groups up to full 64-slot (1 KiB) strides and
       // may read up to ~1 KiB past the group end
@@ -347,16 +349,6 @@ struct BlockStageCtx {
     return it->second;
   }
 
-  const StagedBloom& stage_bloom(const ColumnHeader& ch) {
-    auto it = blooms.find(ch.name);
-    if (it != blooms.end()) return it->second;
-    const std::vector<uint64_t>& words = bloom_host(ch);
-    StagedBloom sb;
-    sb.nwords = uint32_t(words.size());
-    sb.d_words = (const uint64_t*)st->push(words.data(), words.size() * 8, 8);
-    return blooms.emplace(ch.name, sb).first->second;
-  }
-
   const int64_t* stage_timestamps() {
     if (!d_ts) {
       std::vector<int64_t> ts;
@@ -367,15 +359,27 @@ struct BlockStageCtx {
   }
 };
 
+bool h_bloom_all(BlockStageCtx& ctx, const ColumnHeader& ch,
+                 const std::vector<uint64_t>& hashes);
+
+// The leaf's bloom gate (bloomfilter.go:173-191), decided here on the host: a
+// Stage binds one filter to one set of blocks, so the verdict never changes
+// between scans.  Called at every gated leaf kind after the descriptor is
+// filled.  A hit leaves the leaf as staged; a miss (the block cannot hold the
+// leaf's tokens) makes it kModeNone for this block, which the static program
+// evaluation then uses to drop whole blocks.  An empty hash list and a column
+// without bloom words both pass, as containsAll does.  A column that only
+// this leaf uploaded is taken back out of the arena on a miss.
 void set_bloom_gate(DevLeafBlock& lb, BlockStageCtx& ctx, const ColumnHeader& ch,
                     const LeafInfo& li) {
-  const auto& hashes = li.node->token_hashes;
-  if (hashes.empty()) return;
-  const StagedBloom& sb = ctx.stage_bloom(ch);
-  lb.nhashes = uint32_t(hashes.size());
-  lb.hashes = li.d_hashes;
-  lb.bloom = sb.d_words;
-  lb.bloom_words = sb.nwords;
+  if (h_bloom_all(ctx, ch, li.node->token_hashes)) return;
+  lb = DevLeafBlock{};
+  lb.mode = kModeNone;
+  if (ctx.has_fresh && ctx.fresh_col == ch.name) {
+    ctx.st->rollback(ctx.fresh_mark);
+    ctx.cols.erase(ch.name);
+    ctx.has_fresh = false;
+  }
 }
 
 // Shared helper: fixed-width binary equality with header min/max prune
@@ -399,11 +403,11 @@ bool stage_eq_bin(DevLeafBlock& lb, BlockStageCtx& ctx, const ColumnHeader& ch,
   lb.operand_len = uint32_t(bin.size());
   lb.data = sc.d_data;
   set_bloom_gate(lb, ctx, ch, li);
-  return true;
+  return lb.mode == kModeScan;
 }
 
-// Binary equality without a device bloom gate (the gate already ran on the
-// host for the set-family filters).
+// Binary equality without the leaf's own bloom gate (the set-family filters
+// run their gate themselves).
 void stage_eq_bin_nogate(DevLeafBlock& lb, BlockStageCtx& ctx,
                          const ColumnHeader& ch, Stage& st, const bytes& bin) {
   const StagedStrCol& sc = ctx.stage_column(ch);
@@ -687,6 +691,7 @@ void stage_leaf(const LeafInfo& li, BlockStageCtx& ctx, Stage& st, DevLeafBlock&
   const FilterNode& f = *li.node;
   const PartReader& pr = *ctx.pr;
   memset(&lb, 0, sizeof(lb));
+  ctx.has_fresh = false;  // columns cached by earlier leaves stay
 
   auto const_val = [&]() -> std::string {
     std::string v;
@@ -965,22 +970,23 @@ void stage_leaf(const LeafInfo& li, BlockStageCtx& ctx, Stage& st, DevLeafBlock&
       lb.operand = li.d_operand;
       lb.operand_len = uint32_t(li.operand.size());
       lb.data = sc.d_data;
-      set_bloom_gate(lb, ctx, ch, li);
       switch (ch.type) {
         case ValueType::String:
           lb.kind = kScanRegexStr;
           lb.offsets = sc.d_offsets;
-          return;
-        case ValueType::Uint8: lb.kind = kScanRegexU; lb.width = 1; return;
-        case ValueType::Uint16: lb.kind = kScanRegexU; lb.width = 2; return;
-        case ValueType::Uint32: lb.kind = kScanRegexU; lb.width = 4; return;
-        case ValueType::Uint64: lb.kind = kScanRegexU; lb.width = 8; return;
-        case ValueType::Int64: lb.kind = kScanRegexI; lb.width = 8; return;
-        case ValueType::Float64: lb.kind = kScanRegexF64; lb.width = 8; return;
-        case ValueType::IPv4: lb.kind = kScanRegexIp; lb.width = 4; return;
-        case ValueType::TimestampISO8601: lb.kind = kScanRegexIso; lb.width = 8; return;
+          break;
+        case ValueType::Uint8: lb.kind = kScanRegexU; lb.width = 1; break;
+        case ValueType::Uint16: lb.kind = kScanRegexU; lb.width = 2; break;
+        case ValueType::Uint32: lb.kind = kScanRegexU; lb.width = 4; break;
+        case ValueType::Uint64: lb.kind = kScanRegexU; lb.width = 8; break;
+        case ValueType::Int64: lb.kind = kScanRegexI; lb.width = 8; break;
+        case ValueType::Float64: lb.kind = kScanRegexF64; lb.width = 8; break;
+        case ValueType::IPv4: lb.kind = kScanRegexIp; lb.width = 4; break;
+        case ValueType::TimestampISO8601: lb.kind = kScanRegexIso; lb.width = 8; break;
         default: fail("unknown valueType while staging regexp filter");
       }
+      set_bloom_gate(lb, ctx, ch, li);  // last: a miss drops `sc`
+      return;
     }
 
     case FilterNode::Range: {
@@ -1522,7 +1528,6 @@ void stage_leaf(const LeafInfo& li, BlockStageCtx& ctx, Stage& st, DevLeafBlock&
             tmp_li.cname = li.cname;
             tmp_li.operand.assign(phrases[0].begin(), phrases[0].end());
             tmp_li.phrase_flags = phrase_flags_of(phrases[0]);
-            tmp_li.d_hashes = li.d_hashes;
             tmp_li.d_operand =
                 (const uint8_t*)st.push(tmp_li.operand.data(),
                                         tmp_li.operand.size(), 8);
@@ -2175,9 +2180,8 @@ void stage_leaf(const LeafInfo& li, BlockStageCtx& ctx, Stage& st, DevLeafBlock&
           lb.data = sc.d_data;
           lb.offsets = sc.d_offsets;
           if (any) {
-            // override bitmaps ride in the unused bloom-gate fields
-            // (scan_types.h DevLeafBlock comment); nhashes stays 0 so the
-            // bloom gate never fires for these kinds
+            // override bitmaps ride in the side-data fields (scan_types.h
+            // DevLeafBlock comment)
             lb.hashes = (const uint64_t*)st.push(mask.data(), nw * 8, 8);
             lb.bloom = (const uint64_t*)st.push(val.data(), nw * 8, 8);
           }
@@ -2206,10 +2210,6 @@ void stage_leaf(const LeafInfo& li, BlockStageCtx& ctx, Stage& st, DevLeafBlock&
           if (!tmp_li.operand.empty()) {
             tmp_li.d_operand = (const uint8_t*)st.push(tmp_li.operand.data(),
                                                        tmp_li.operand.size(), 8);
-          }
-          if (!tmp.token_hashes.empty()) {
-            tmp_li.d_hashes = (const uint64_t*)st.push(
-                tmp.token_hashes.data(), tmp.token_hashes.size() * 8, 8);
           }
           stage_leaf(tmp_li, ctx, st, lb);
           return;
@@ -2384,9 +2384,8 @@ void stage_leaf(const LeafInfo& li, BlockStageCtx& ctx, Stage& st, DevLeafBlock&
 // Blocks whose program value is statically 0 never reach the kernel: their
 // chunks are compacted out of the dispatch and their bitmap words zeroed
 // once (the reference's header prunes have the same effect — e.g.
-// filter_time.go:114-137 zeroes the bitmap without touching rows).  Bloom
-// gates can only turn a kModeScan leaf into 0 at run time, so they keep
-// value 2 here (bloom has no false negatives; the static result is sound).
+// filter_time.go:114-137 zeroes the bitmap without touching rows).  A leaf
+// whose bloom gate missed at staging is kModeNone, value 0 here.
 static int static_program_value(const std::vector<DevOp>& ops,
                                 const DevLeafBlock* lbs) {
   std::vector<int> stack;
@@ -2451,7 +2450,7 @@ Stage* build_stage_refs(std::vector<std::pair<VqlPart*, long>> refs,
   for (long b = 0; b < nblocks; b++) rows += bh_of(b).rows_count;
   st->rows = rows;
 
-  // leaf operands + probe hashes (block-independent)
+  // leaf operands (block-independent)
   std::vector<LeafInfo> leaf_infos{filter->leaves.size()};
   for (size_t i = 0; i < filter->leaves.size(); i++) {
     LeafInfo& li = leaf_infos[i];
@@ -2517,10 +2516,6 @@ Stage* build_stage_refs(std::vector<std::pair<VqlPart*, long>> refs,
     }
     if (!li.operand.empty()) {
       li.d_operand = st->push(li.operand.data(), li.operand.size(), 8);
-    }
-    if (!li.node->token_hashes.empty()) {
-      li.d_hashes = (const uint64_t*)st->push(li.node->token_hashes.data(),
-                                              li.node->token_hashes.size() * 8, 8);
     }
   }
 
